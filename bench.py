@@ -9,7 +9,8 @@ Other configs (--config): c2 = the same at 10M keys (R = 2^26); c3 = sliding 10 
 double values, sum/min/max/count; c4 = Zipf(1.2) keys, timestamps up to 300 ms out of order, watermark
 lag 50 ms, allowed lateness 100 ms (per-element late fires and late drops; R = 2^25), sum/count.
 A step = one batch of 2^22 events per GPU pushed through the engine + its watermark (fire/purge).
-Inputs are generated on the GPU and resident in HBM before the timed region.
+Inputs are generated on the GPU and resident in HBM before the timed region (96 MiB per step; a plain
+run of more steps than fit HBM reuses them as a ring, see input_ring).
 
 Multi-GPU (torchrun, one process per GPU): every rank is a source subtask producing its own 2^22
 events per step (weak scaling); records are routed to the key-group owner (maxParallelism 128) by
@@ -17,14 +18,23 @@ the keyBy exchange (HIP partition kernel + RCCL all-to-all) and the watermark is
 
 Roofline: algorithmic bytes per step = 24 B x events + 96 B (112 B for C3) x fired
 panes; the headline `achieved` divides them by the whole step time (ms_per_step), so every kernel of
-the path and the gaps between them count.  Per-kernel device times (HIP events on the stream each runs
-on, measured after the timed region) and the PMC HBM traffic of the committed rocprofv3 summary of this
-library build are reported beside it.
+the path and the gaps between them count.
+
+A plain run sets up, warms up, times the --steps steps and prints the line: the headline value,
+ms_per_step and the whole-step roofline.  --full adds, after the timed region, everything that takes
+runs of its own: per-kernel device times (HIP events on the stream each runs on) with the PMC HBM
+traffic of the committed rocprofv3 summary of this library build, the PCIe-inclusive, wire-decode and
+drained-results legs, the CPU baseline and the checks against the pushed values / the oracle.
+
+--dump-outputs DIR writes what the timed path handed its caller (the fired results collected after
+the timed region, see dump_outputs) as DIR/<column>.npy; the inputs are a pure function of the
+arguments, so two builds can be compared output for output.
 
 Prints ONE JSON line (rank 0).
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -66,6 +76,11 @@ CONFIGS = {
 }
 
 
+FULL_LEGS = {"prof_steps": 8, "decode_steps": 4, "drain_steps": 32, "h2d_steps": 8, "cpu_sample": 1 << 25}
+DUMP_BYTES = 32 << 20      # --dump-outputs budget over all columns (float64)
+RING_BATCHES = 256         # input batches of the ring that serves more steps than fit HBM (its cost is per step)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -73,20 +88,37 @@ def parse():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--config", default="c1", choices=sorted(CONFIGS))
     ap.add_argument("--ingest-mode", type=int, default=0)
-    ap.add_argument("--cpu-sample", type=int, default=1 << 25, help="events in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs that take runs of their own: per-kernel device "
+                         "times and PMC traffic, H2D, wire decode, drained results, the CPU baseline and the checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results the timed path fired (collected after the timed region) as DIR/<column>.npy")
+    ap.add_argument("--resident-batches", type=int, default=None,
+                    help="input batches that may stay in HBM (default: what fits the free memory); a plain run of more "
+                         "steps reuses a ring of them (see input_ring)")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="--full: events in the CPU baseline sample (default 2^25, 0 = skip)")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--force-exchange", action="store_true",
                     help="diagnostics: run the keyBy exchange (partition + RCCL all-to-all + MIN all-reduce) at N=1 too")
-    ap.add_argument("--prof-steps", type=int, default=8,
-                    help="steps after the timed region run with per-kernel device-time events (roofline); "
+    ap.add_argument("--prof-steps", type=int, default=None,
+                    help="--full (default 8): steps after the timed region run with per-kernel device-time events (roofline); "
                          "timed events serialise kernels, so the timed region runs without them")
-    ap.add_argument("--decode-steps", type=int, default=4,
-                    help="wire-format decode leg (fw_decode of the batch as Flink network bytes; 0 = skip)")
-    ap.add_argument("--drain-steps", type=int, default=32,
-                    help="steps of the leg that collects fired results to the host after every step (0 = skip)")
-    ap.add_argument("--h2d-steps", type=int, default=8,
-                    help="steps after the timed region pushed from pinned host columns (PCIe-inclusive rate; 0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--decode-steps", type=int, default=None,
+                    help="--full (default 4): wire-format decode leg (fw_decode of the batch as Flink network bytes; 0 = skip)")
+    ap.add_argument("--drain-steps", type=int, default=None,
+                    help="--full (default 32): steps of the leg that collects fired results to the host after every step (0 = skip)")
+    ap.add_argument("--h2d-steps", type=int, default=None,
+                    help="--full (default 8): steps after the timed region pushed from pinned host columns (PCIe-inclusive rate; 0 = skip)")
+    args = ap.parse_args()
+    for name, default in FULL_LEGS.items():   # the legs beyond the headline run only under --full
+        given = getattr(args, name)
+        if not args.full and given:
+            ap.error(f"--{name.replace('_', '-')} {given} needs --full")
+        setattr(args, name, (default if given is None else given) if args.full else 0)
+    if not args.full:
+        args.no_check = True
+    return args
 
 
 def dist_init(args):
@@ -189,6 +221,103 @@ def traffic_of(pmc, short):
     return None
 
 
+def kernel_roofline(args, prof, form, ev_gpu, alg_step):
+    """The per-kernel part of the roofline (--full): device time per launch from the profiled steps after the timed
+    region, and the PMC HBM traffic of the committed summary of this library build."""
+    def per(ph):
+        n_ = prof.launches[ph]
+        return (prof.ms[ph] / n_ if n_ else 0.0), n_
+    route_ms, _ = per(_abi.FW_PHASE_INGEST)
+    agg_ms, _ = per(_abi.FW_PHASE_AGGREGATE)
+    wm_ms, wm_n = per(_abi.FW_PHASE_FIRE)
+    late_ms, late_n = per(_abi.FW_PHASE_LATE)
+    wm_per_step = wm_n / max(args.prof_steps, 1)
+    pmc, pmc_src = pmc_traffic(args.config)
+    kernels = {}
+    names = ([("k_route", route_ms, 1.0), ("k_aggregate", agg_ms, 1.0)] if form == 2 else
+             [("k_ingest_direct", route_ms, 1.0)])
+    names.append(("k_watermark", wm_ms, wm_per_step))
+    for name, ms, per_step in names:
+        tr = traffic_of(pmc, name)
+        kernels[name] = {"ms": ms, "launches_per_step": per_step,
+                         "achieved_GBs": (24.0 * ev_gpu / (ms / 1e3) / 1e9) if ms and name != "k_watermark" else None,
+                         "traffic_bytes_per_launch": tr}
+        if kernels[name]["achieved_GBs"]:
+            kernels[name]["frac"] = kernels[name]["achieved_GBs"] / HBM_PEAK_GBS
+    if late_n:
+        kernels["late_path"] = {"ms": late_ms, "launches_per_step": late_n / max(args.prof_steps, 1)}
+    ingest = [n for n, _, _ in names if n != "k_watermark"]
+    dom = max(ingest, key=lambda n: kernels[n]["ms"])
+    traffic_step = None
+    if pmc and all(kernels[n]["traffic_bytes_per_launch"] for n in ingest):
+        traffic_step = sum(kernels[n]["traffic_bytes_per_launch"] * kernels[n]["launches_per_step"] for n in kernels
+                           if kernels[n].get("traffic_bytes_per_launch"))
+    return {"traffic": traffic_step,
+            "traffic_unit": "HBM bytes per step: sum over kernels of PMC bytes per launch (FETCH_SIZE x2 + "
+                            "WRITE_SIZE, rocprofv3 --pmc) x launches per step",
+            "traffic_ratio": (traffic_step / alg_step) if traffic_step else None,
+            "traffic_source": pmc_src,
+            "dominant_kernel": dom, "kernels": kernels,
+            "device_time_source": f"HIP events around each kernel on its stream, {args.prof_steps} "
+                                  "batches after the timed region, one batch at a time"}
+
+
+def input_ring(args, C, n_in, dev):
+    """0 when the run's n_in input batches (24 B x batch each) all stay resident in HBM: the run the headline is
+    quoted on, nothing reused.  Otherwise --steps asks for more than fits, and the size of the ring that serves
+    it: an even number of batches spanning whole event-time milliseconds, so that batch j + ring is batch j
+    again that much later.  The timed region then also advances the timestamps of one half of the ring (a side
+    stream, 64 MiB of HBM traffic per step at 2^22 events) while the other half runs, and synchronises with the
+    engine once per half, which a run on resident inputs never does: C1 measured 85 us per step over 16000 steps
+    against 73 us over 2000 resident ones, so compare ring runs only with ring runs."""
+    cap = args.resident_batches
+    if cap is None:   # what the free memory holds, less 1 GiB for the generator's temporaries
+        cap = (torch.cuda.mem_get_info(dev)[0] - (1 << 30)) // (24 * C["batch"])
+    if n_in <= cap:
+        return 0
+    q = 2 * (C["rate"] // math.gcd(C["rate"], C["batch"] * 1000))
+    return max(q, min(cap, RING_BATCHES) // q * q)
+
+
+OUT_COLUMNS = ("key", "f1", "ts", "win_start", "sum_i64", "min_i64", "max_i64", "count", "sum_f64", "min_f64", "max_f64")
+
+
+def dump_outputs(out_dir, res, rank=0):
+    """Write the results the timed path handed its caller as out_dir/<column>.npy (float64), one row per fired result.
+
+    `res` is the collect after the timed region: every result fired since the warm-up's last step.  The rows of the
+    most recently fired windows are kept, as many whole windows (distinct result timestamps, the latest first) as
+    fit DUMP_BYTES, and at least one; a single window larger than that is cut to a seeded sample of its rows.  The
+    order in which a watermark's results reach the output log is not part of the contract, so the rows are sorted
+    (by ts, key, then the other columns).  key, f1, ts and counts are exact in float64; a wrapping long sum is
+    rounded, so its low 32 bits are written beside it (<column>_lo32) to keep the comparison exact."""
+    names = [c for c in OUT_COLUMNS if res.get(c) is not None and len(res[c]) == res["n"]]
+    n = int(res["n"])
+    ts = res["ts"]
+    cols64 = [c for c in names if c.endswith("_i64")]
+    row_bytes = 8 * (len(names) + len(cols64))
+    max_rows = max(1, DUMP_BYTES // row_bytes)
+    keep = np.zeros(0, np.int64)
+    if n:
+        stamps, counts = np.unique(ts, return_counts=True)
+        tail = np.cumsum(counts[::-1])   # rows of the latest 1, 2, ... windows
+        k = max(1, int(np.searchsorted(tail, max_rows, side="right")))
+        keep = np.flatnonzero(ts >= stamps[-k])
+    sub = {c: res[c][keep] for c in names}
+    if len(keep):
+        order = np.lexsort([sub[c] for c in reversed(["ts", "key"] + [c for c in names if c not in ("ts", "key")])])
+        if len(order) > max_rows:
+            order = order[np.sort(np.random.default_rng(0).choice(len(order), max_rows, replace=False))]
+        sub = {c: a[order] for c, a in sub.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    for c in names:
+        np.save(os.path.join(out_dir, f"{c}{tag}.npy"), sub[c].astype(np.float64))
+        if c in cols64:
+            lo32 = sub[c].view(np.uint64) & np.uint64(0xFFFFFFFF)
+            np.save(os.path.join(out_dir, f"{c}_lo32{tag}.npy"), lo32.astype(np.float64))
+
+
 def main():
     args = parse()
     world, rank, local = dist_init(args)
@@ -222,14 +351,35 @@ def main():
 
     # resident synthetic input: rank r is source subtask r; its i-th event is global index i*world + r
     # (the interleaving keeps event time aligned across sources)
+    n_in = args.warmup + args.steps + args.prof_steps
+    ring = input_ring(args, C, n_in, dev)   # 0: every batch resident, as the headline is quoted
+    if ring and (world > 1 or args.force_exchange or args.full):
+        sys.exit(f"bench.py: {n_in} input batches do not fit resident; the ring of {ring} serves only a plain --gpus 1 run")
     cols = []
-    for j in range(args.warmup + args.steps + args.prof_steps):
+    for j in range(ring or n_in):
         k, t, v = stream(j * batch * world, batch * world, n_keys, rate, T0, device=dev, value_type=vt,
                          zipf=C["zipf"], ooo=C["ooo"])
         if world > 1:
             k, t, v = k[rank::world].contiguous(), t[rank::world].contiguous(), v[rank::world].contiguous()
         cols.append((k, t, v))
     torch.cuda.synchronize()
+    if ring:
+        # batch j >= ring is batch j - ring again (its keys and values) a whole number of event-time milliseconds
+        # later: each half of the ring has its timestamps advanced on a side stream while the other half runs
+        half = ring // 2
+        ring_ms = ring * batch * 1000 // rate
+        side = torch.cuda.Stream(dev)
+        advanced = [None, None]
+
+        def recycle(j):
+            h = (j // half) % 2
+            if advanced[h] is not None:   # the half about to run: its timestamps are advanced by now
+                torch.cuda.current_stream(dev).wait_event(advanced[h])
+            if j >= half:                 # the half that just ran: read to the end, free to be advanced
+                eng.sync()
+                with torch.cuda.stream(side):
+                    torch._foreach_add_([t for _, t, _ in cols[(1 - h) * half:(2 - h) * half]], ring_ms)
+                    advanced[1 - h] = side.record_event()
 
     exch = None
     if world > 1 or args.force_exchange:
@@ -240,7 +390,10 @@ def main():
         # source watermark after batch j: max ts seen - lag (BoundedOutOfOrdernessTimestampExtractor)
         return int(T0 + (((j + 1) * batch * world - 1) * 1000) // rate) - C["wm_lag"]
 
-    def step(j, k, t, v):
+    def step(j):
+        if ring and j % half == 0:
+            recycle(j)
+        k, t, v = cols[j % len(cols)]
         if exch is None:
             eng.push(k, t, v)
             eng.advance_watermark(wm_of(j))
@@ -260,7 +413,7 @@ def main():
             drain()
             eng.sync()
             collected.append(eng.collect())
-        step(j, *cols[j])
+        step(j)
     drain()
     eng.sync()
     torch.cuda.synchronize()
@@ -269,7 +422,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for j in range(args.warmup, args.warmup + args.steps):
-        step(j, *cols[j])
+        step(j)
     drain()
     t_enq = time.perf_counter() - t0   # host time to enqueue the K steps (host-bound if close to dt)
     torch.cuda.synchronize()      # device-wide: covers the engine's own streams
@@ -277,21 +430,26 @@ def main():
     dt = time.perf_counter() - t0
     st1 = eng.stats()
     fired_per_step = (st1["panes_fired"] - st0["panes_fired"]) / args.steps
-    collected.append(eng.collect())
+    if args.full or args.dump_outputs:   # what the timed path fired (and the warm-up's last step): its caller's results
+        collected.append(eng.collect())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, collected[-1], rank)
 
     # per-kernel device time on the continuation of the same stream (untimed)
-    eng.lib.fw_set_profiling(eng.h, 1)
-    eng.lib.fw_get_profile(eng.h, _abi.FwProfile())  # reset counters
-    j0 = args.warmup + args.steps
-    for j in range(j0, j0 + args.prof_steps):
-        step(j, *cols[j])
-        drain()
-        eng.sync()   # isolate the kernels (no route/aggregate overlap across batches while timing them)
-    prof = _abi.FwProfile()
-    eng.lib.fw_get_profile(eng.h, prof)
-    eng.lib.fw_set_profiling(eng.h, 0)
-    eng.sync()
-    collected.append(eng.collect())
+    prof = None
+    if args.full:
+        eng.lib.fw_set_profiling(eng.h, 1)
+        eng.lib.fw_get_profile(eng.h, _abi.FwProfile())  # reset counters
+        j0 = args.warmup + args.steps
+        for j in range(j0, j0 + args.prof_steps):
+            step(j)
+            drain()
+            eng.sync()   # isolate the kernels (no route/aggregate overlap across batches while timing them)
+        prof = _abi.FwProfile()
+        eng.lib.fw_get_profile(eng.h, prof)
+        eng.lib.fw_set_profiling(eng.h, 0)
+        eng.sync()
+        collected.append(eng.collect())
 
     # PCIe-inclusive ingest: the same kind of batch pushed from pinned host columns (FW_MEM_HOST)
     h2d = None
@@ -492,14 +650,6 @@ def main():
     value = events / dt
     ms_step = dt * 1e3 / args.steps
 
-    def per(ph):
-        n_ = prof.launches[ph]
-        return (prof.ms[ph] / n_ if n_ else 0.0), n_
-    route_ms, _ = per(_abi.FW_PHASE_INGEST)
-    agg_ms, _ = per(_abi.FW_PHASE_AGGREGATE)
-    wm_ms, wm_n = per(_abi.FW_PHASE_FIRE)
-    late_ms, late_n = per(_abi.FW_PHASE_LATE)
-    wm_per_step = wm_n / max(args.prof_steps, 1)
     # algorithmic bytes: 24 B per event (key, ts, value) + per fired pane 96 B (C3:
     # 112 B); at N > 1 the keyBy exchange sends each GPU's (N-1)/N share of its events to the other GPUs (21 B/event
     # at N = 8: SURVEY.md 8(e)), which the receivers write to HBM: B_alg = 24 N + 96 P_fired + 24 (N-1)/N N
@@ -507,26 +657,9 @@ def main():
     xchg_step = 24.0 * ev_gpu * (world - 1) / world if world > 1 else 0.0
     alg_step = 24.0 * ev_gpu + C["pane_bytes"] * fired_per_step / max(world, 1) + xchg_step
     achieved = alg_step / (ms_step / 1e3) / 1e9
-    pmc, pmc_src = pmc_traffic(args.config)
-    kernels = {}
-    names = ([("k_route", route_ms, 1.0), ("k_aggregate", agg_ms, 1.0)] if form == 2 else
-             [("k_ingest_direct", route_ms, 1.0)])
-    names.append(("k_watermark", wm_ms, wm_per_step))
-    for name, ms, per_step in names:
-        tr = traffic_of(pmc, name)
-        kernels[name] = {"ms": ms, "launches_per_step": per_step,
-                         "achieved_GBs": (24.0 * ev_gpu / (ms / 1e3) / 1e9) if ms and name != "k_watermark" else None,
-                         "traffic_bytes_per_launch": tr}
-        if kernels[name]["achieved_GBs"]:
-            kernels[name]["frac"] = kernels[name]["achieved_GBs"] / HBM_PEAK_GBS
-    if late_n:
-        kernels["late_path"] = {"ms": late_ms, "launches_per_step": late_n / max(args.prof_steps, 1)}
-    ingest = [n for n, _, _ in names if n != "k_watermark"]
-    dom = max(ingest, key=lambda n: kernels[n]["ms"])
-    traffic_step = None
-    if pmc and all(kernels[n]["traffic_bytes_per_launch"] for n in ingest):
-        traffic_step = sum(kernels[n]["traffic_bytes_per_launch"] * kernels[n]["launches_per_step"] for n in kernels
-                           if kernels[n].get("traffic_bytes_per_launch"))
+    per_kernel = {}
+    if prof is not None:   # --full: the per-kernel figures of the profiled steps and the committed PMC traffic
+        per_kernel = kernel_roofline(args, prof, form, ev_gpu, alg_step)
     line = {
         "metric": "events/sec (whole node) keyed 1s tumbling sum; % of HBM roofline",
         "value": value,
@@ -545,17 +678,10 @@ def main():
                    "batch_per_gpu": batch, "keys": n_keys, "max_parallelism": mp, "parallelism": f"kg{world}",
                    "reduce": f"{'/'.join(fields)} over {vt}, f1 = first arrival"},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_step,
+                     "frac": achieved / HBM_PEAK_GBS,
                      "scope": "whole step: algorithmic bytes of one batch (24 B/event + pane bytes x fired panes) "
                               "over ms_per_step, every kernel and gap included",
-                     "algorithmic_bytes_per_step": alg_step, "fired_panes_per_step": fired_per_step,
-                     "traffic_unit": "HBM bytes per step: sum over kernels of PMC bytes per launch (FETCH_SIZE x2 + "
-                                     "WRITE_SIZE, rocprofv3 --pmc) x launches per step",
-                     "traffic_ratio": (traffic_step / alg_step) if traffic_step else None,
-                     "traffic_source": pmc_src,
-                     "dominant_kernel": dom, "kernels": kernels,
-                     "device_time_source": f"HIP events around each kernel on its stream, {args.prof_steps} "
-                                           "batches after the timed region, one batch at a time"},
+                     "algorithmic_bytes_per_step": alg_step, "fired_panes_per_step": fired_per_step, **per_kernel},
         "check": check,
         "stats": {k: stats[k] for k in ("records_in", "records_late", "panes_fired", "late_fires", "ingest_form")},
         "host_enqueue_ms_per_step": t_enq * 1e3 / args.steps,

@@ -2,7 +2,7 @@
 # A/B of FW_DEBUG_AGG knobs: a short bench run (throughput + per-kernel device times) and one
 # FETCH_SIZE --pmc pass (no trace domains) per knob value.  Usage: KNOBS="0 32" bash tools/ab_knobs.sh
 REPO="${GRAFT_REPO_ROOT:-/root/repo}"; cd "$REPO"; export TMPDIR=/tmp
-ARGS=${AB_ARGS:-"--steps 32 --warmup 4 --cpu-sample 0 --no-check"}
+ARGS=${AB_ARGS:-"--full --steps 32 --warmup 4 --cpu-sample 0 --no-check"}
 for d in ${KNOBS:-0 32}; do
   FW_DEBUG_AGG=$d timeout -k 10 180 python3 bench.py $ARGS > gpurun_out/ab_$d.log 2>&1 || { echo "bench $d failed"; tail -5 gpurun_out/ab_$d.log; exit 1; }
   python3 - gpurun_out/ab_$d.log $d <<'PY'

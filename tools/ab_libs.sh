@@ -2,7 +2,7 @@
 # A/B of two builds of the engine library in one run: bench throughput, per-kernel device time and the
 # host enqueue time per step.  Usage: LIB_B=flink_amd/lib/old/libflink_window.so bash tools/ab_libs.sh
 REPO="${GRAFT_REPO_ROOT:-/root/repo}"; cd "$REPO"; export TMPDIR=/tmp
-ARGS=${AB_ARGS:-"--steps 64 --warmup 8 --cpu-sample 0 --no-check"}
+ARGS=${AB_ARGS:-"--full --steps 64 --warmup 8 --cpu-sample 0 --no-check"}
 for rep in 1 2; do
   for lib in flink_amd/lib/libflink_window.so ${LIB_B}; do
     tag=$(basename $(dirname $lib))_$rep

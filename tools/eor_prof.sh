@@ -1,8 +1,8 @@
-# round-end measurement: rocprofv3 trace + PMC passes (tools/profile_round.sh), then the bench lines of every
+# round-end measurement: rocprofv3 trace + PMC passes (tools/profile_round.sh), then the full bench lines of every
 # config; each GPU step under its own limit, stopping at the first failure
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."; OUT="${OUT:-bench_out}"; mkdir -p "$OUT"
 bash tools/profile_round.sh || exit $?
 for c in ${CONFIGS:-c1 c2 c3 c4}; do
-  timeout -k 10 300 python bench.py --config $c ${BENCH_ARGS} > gpurun_out/eor_bench_$c.log 2>&1; rc=$?
-  echo "bench $c rc=$rc"; tail -c 400 gpurun_out/eor_bench_$c.log; echo; [ $rc -eq 0 ] || exit $rc
+  timeout -k 10 300 python bench.py --full --config $c ${BENCH_ARGS} > "$OUT/eor_bench_$c.log" 2>&1; rc=$?
+  echo "bench $c rc=$rc"; tail -c 400 "$OUT/eor_bench_$c.log"; echo; [ $rc -eq 0 ] || exit $rc
 done

@@ -4,7 +4,7 @@
 # gpurun_out/prof_*; copy the summaries to profiles/.
 REPO="${GRAFT_REPO_ROOT:-/root/repo}"
 cd "$REPO"
-ARGS=${PROF_ARGS:-"--steps 16 --warmup 4 --prof-steps 0 --cpu-sample 0 --no-check"}
+ARGS=${PROF_ARGS:-"--full --steps 16 --warmup 4 --prof-steps 0 --cpu-sample 0 --no-check"}
 export TMPDIR=/tmp
 rm -rf gpurun_out/prof_trace gpurun_out/prof_fetch gpurun_out/prof_write
 md5sum flink_amd/lib/libflink_window.so | cut -d' ' -f1 > gpurun_out/prof_md5.txt
