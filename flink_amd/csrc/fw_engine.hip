@@ -3301,6 +3301,16 @@ struct ListDev {
   int64_t fcap;
 };
 
+// SessDev::lmeta's words (the checkpoint logs' bookkeeping)
+enum SessLogMeta {
+  LM_OPRUNED = 0,    // entries not carried over by the orphan log's roll-overs so far (diagnostics)
+  LM_NSPRUNED = 1,   // ... from the namespace log
+  LM_OLOST = 2,      // the largest cleanup time of a dropped orphan entry (INT64_MIN: none)
+  LM_NSLIVE = 3,     // flagged namespaces (nsdrop) still live at the last scan (k_sess_ns_lost)
+  LM_NSDROP = 4,     // a namespace entry was dropped since the last scan found none live
+  LM_WORDS = 8
+};
+
 // session windows (fw_session.hip): per key id `sw` window slots, key-major [D + 1][sw]
 constexpr int SESS_SW_DEFAULT = 32, SESS_SW_MAX = 256;   // in-flight session windows per key
 struct SessDev {
@@ -3339,9 +3349,21 @@ struct SessDev {
   int64_t* olog;
   unsigned long long* olog_n;
   int64_t olog_cap;
+  // both logs are rolled over at each watermark (k_sess_log_roll) into their spare buffers otmp / nstmp, which the
+  // host then makes the logs: only the entries a snapshot can still need are carried over — orphan entries whose
+  // cleanup time lies ahead, namespace entries whose hashed namespace still has live entries.  An entry that finds
+  // its log full is dropped and remembered, so that a snapshot fails (FW_ERR_CAPACITY) exactly while it would miss
+  // the entry: the largest cleanup time of a dropped orphan entry, and nsdrop[slot] set for a dropped namespace
+  // entry's hashed namespace.  lmeta: the words SessLogMeta names
+  long long* lmeta;
+  uint8_t* nsdrop;
+  int64_t *otmp, *nstmp;
+  unsigned long long *otmp_n, *nstmp_n;
+  int64_t late;     // the allowed lateness (a logged orphan's cleanup time)
   int32_t ckpt;     // checkpoint bookkeeping on (FW_SESS_CKPT=0: off; fw_snapshot_kg_flink / restore then fail)
-  int64_t* rlist;   // slots a watermark retired (k_sess_wm -> k_sess_ns_retire)
-  unsigned long long* rlist_n;
+  int64_t* rlist;   // slots a watermark retired (k_sess_wm -> k_sess_ns_retire, k_sess_log_roll)
+  int64_t* rslot;   // ... and each one's hashed namespace (k_sess_ns_retire -> k_sess_log_roll)
+  unsigned long long *rlist_n, *rlist_n2;   // (rlist_n2: the next watermark's count, zeroed meanwhile)
   int64_t rlist_cap;
   // list state (FW_AGG_LIST): per slot the window's elements as a linked list through an element pool of pcap
   // entries, handed out from a ring of free entry indices (freeq; pool[0] head, pool[1] end of the free ones,
@@ -3367,20 +3389,31 @@ __device__ __forceinline__ uint64_t sess_ns_slot(const SessDev& d, int32_t kg, i
 __device__ __forceinline__ void sess_ns_add(const SessDev& d, int32_t kg, int64_t sws) {
   atomicAdd(&d.nscnt[sess_ns_slot(d, kg, sws)], 1);
 }
-__device__ __forceinline__ void sess_ns_remove(const SessDev& d, int32_t kg, int64_t key, int64_t x, int64_t r) {
-  const int64_t sws = d.sws[x];
-  if (atomicSub(&d.nscnt[sess_ns_slot(d, kg, sws)], 1) <= 1) return;   // the namespace's last entry: it ends here
-  const unsigned long long pos = atomicAdd(d.nslog_n, 1ull);
-  if ((int64_t)pos >= d.nslog_cap) return;   // (overflow: the snapshot falls back to the oldest live entry)
-  int64_t* l = d.nslog + 4 * pos;
+__device__ __forceinline__ void sess_ns_log(const SessDev& d, int64_t* log, unsigned long long* log_n, uint64_t slot,
+                                            int64_t key, int64_t x, int64_t r) {
+  const unsigned long long pos = atomicAdd(log_n, 1ull);
+  if ((int64_t)pos >= d.nslog_cap) {   // overflow: snapshots fail until this namespace has ended
+    d.nsdrop[slot] = 1;
+    d.lmeta[LM_NSDROP] = 1;
+    return;
+  }
+  int64_t* l = log + 4 * pos;
   l[0] = key;
-  l[1] = sws;
+  l[1] = d.sws[x];
   l[2] = d.swc[x];
   l[3] = r;
 }
+__device__ __forceinline__ void sess_ns_remove(const SessDev& d, int32_t kg, int64_t key, int64_t x, int64_t r) {
+  const uint64_t slot = sess_ns_slot(d, kg, d.sws[x]);
+  if (atomicSub(&d.nscnt[slot], 1) <= 1) return;   // the namespace's last entry: it ends here
+  sess_ns_log(d, d.nslog, d.nslog_n, slot, key, x, r);
+}
 __device__ __forceinline__ void sess_orphan(const SessDev& d, int64_t key, int64_t start, int64_t end, int64_t seq) {
   const unsigned long long pos = atomicAdd(d.olog_n, 1ull);
-  if ((int64_t)pos >= d.olog_cap) return;   // (overflow: the snapshot reports FW_ERR_CAPACITY)
+  if ((int64_t)pos >= d.olog_cap) {   // overflow: snapshots fail until the watermark reaches this timer
+    atomicMax(&d.lmeta[LM_OLOST], (long long)cleanup_time(jsub(end, 1), d.late));
+    return;
+  }
   int64_t* l = d.olog + 4 * pos;
   l[0] = key;
   l[1] = start;
@@ -3465,7 +3498,11 @@ struct fw_engine {
   // advance; keys whose set a restored timer fetched when it fired (key -> (ordinal, timer time))
   std::vector<std::array<int64_t, 4>> sess_orphans;
   std::set<std::array<int64_t, 3>> sess_rorphans;
+  // (sess_adv is kept only while restored timers are pending — the last of them fires at sess_rorph_ct — and cut
+  // back to its last entry whenever the fired ones are taken out: session_fire_rorphans)
   std::vector<std::pair<int64_t, int64_t>> sess_adv;
+  int64_t sess_rorph_ct = INT64_MIN;
+  int64_t sess_olog_drained = 0;   // orphan log entries snapshots have drained (fw_debug_session_logs)
   std::map<int64_t, std::pair<int64_t, int64_t>> sess_touch_adj;
   int64_t sess_pool_used = 0;   // session list state: pool entries a restore laid elements in
   struct SessHost {
@@ -3690,6 +3727,7 @@ static thread_local std::string g_create_error;
 int session_create(fw_engine* e);
 int session_push(fw_engine* e, const fw::BatchIn& b);
 int session_watermark(fw_engine* e, int64_t wm);
+int session_ns_lost(fw_engine* e, bool* lossy);
 // list state (fw_list.hip)
 int list_create(fw_engine* e);
 int list_push(fw_engine* e, const fw::BatchIn& b);
@@ -5505,7 +5543,7 @@ static int session_download(fw_engine* e) {
   HIPCHK(e, hipMemcpy(h.kacc.data(), d.kacc, 4 * rows, hipMemcpyDeviceToHost));
   unsigned long long nl = 0;
   HIPCHK(e, hipMemcpy(&nl, d.nslog_n, 8, hipMemcpyDeviceToHost));
-  h.nslog_over = (int64_t)nl > d.nslog_cap;
+  if (int rc = session_ns_lost(e, &h.nslog_over)) return rc;   // a live namespace lacks a dropped entry
   HIPCHK(e, get(h.nslog, d.nslog, 4 * (size_t)std::min<int64_t>((int64_t)nl, d.nslog_cap)));
   h.live.assign(rows * (size_t)d.nw, 0);
   h.trig.assign(rows * (size_t)d.nw, 0);
@@ -5514,6 +5552,23 @@ static int session_download(fw_engine* e) {
   h.epoch = e->state_epoch;
   h.wm = e->cur_wm;
   return FW_OK;
+}
+
+// restored purged sessions' cleanup timers the watermark has reached: each fetched its key's set when it fired
+// (onEventTime -> getMergingWindowSet), at the ordinal of the advance that reached it.  The ones still pending lie
+// ahead of every advance so far, so only the last advance is kept
+static void session_fire_rorphans(fw_engine* e) {
+  const int64_t lateness = e->cfg.allowed_lateness;
+  for (auto it = e->sess_rorphans.begin(); it != e->sess_rorphans.end();) {
+    const int64_t ct = fw::cleanup_time(fw::jsub((*it)[2], 1), lateness);
+    if (ct > e->cur_wm) { ++it; continue; }
+    int64_t ord = 0;
+    for (const auto& a : e->sess_adv) if (a.first >= ct) { ord = a.second; break; }
+    auto adj = e->sess_touch_adj.find((*it)[0]);
+    if (adj == e->sess_touch_adj.end() || std::make_pair(ord, ct) < adj->second) e->sess_touch_adj[(*it)[0]] = {ord, ct};
+    it = e->sess_rorphans.erase(it);
+  }
+  if (e->sess_adv.size() > 1) e->sess_adv.erase(e->sess_adv.begin(), e->sess_adv.end() - 1);
 }
 
 static int session_reject_config(fw_engine* e) {
@@ -5538,29 +5593,29 @@ static int session_snapshot_kg_flink(fw_engine* e, int32_t kg, const fw_state_la
   const fw_config& c = e->cfg;
   const size_t kgi = (size_t)(kg - s.kg_start);
   const bool orphans = c.trigger == FW_TRIGGER_PURGING_EVENT_TIME && c.allowed_lateness > 0;
-  if (orphans) {   // purged sessions' cleanup timers logged since the last snapshot
+  if (h.nslog_over)
+    return reject(e, FW_ERR_CAPACITY, "the shared-namespace log overflowed: the order of a namespace still live is unknown until it ends");
+  if (orphans) {   // purged sessions' cleanup timers logged since the last snapshot (or the log's last pruning)
     unsigned long long no = 0;
+    long long lost = INT64_MIN;
     HIPCHK(e, hipMemcpy(&no, d.olog_n, 8, hipMemcpyDeviceToHost));
-    if ((int64_t)no > d.olog_cap)
-      return reject(e, FW_ERR_CAPACITY, "more purged sessions since the last snapshot than the orphan timer log holds");
-    std::vector<int64_t> ol(4 * (size_t)no);
-    if (no) HIPCHK(e, hipMemcpy(ol.data(), d.olog, 8 * ol.size(), hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(&lost, d.lmeta + LM_OLOST, 8, hipMemcpyDeviceToHost));
+    const size_t take = (size_t)std::min<int64_t>((int64_t)no, d.olog_cap);   // (entries past the cap were dropped)
+    std::vector<int64_t> ol(4 * take);
+    if (take) HIPCHK(e, hipMemcpy(ol.data(), d.olog, 8 * ol.size(), hipMemcpyDeviceToHost));
     HIPCHK(e, hipMemset(d.olog_n, 0, 8));
-    for (size_t j = 0; j < (size_t)no; ++j) e->sess_orphans.push_back({ol[4 * j], ol[4 * j + 1], ol[4 * j + 2], ol[4 * j + 3]});
+    e->sess_olog_drained += (int64_t)no;
+    for (size_t j = 0; j < take; ++j) e->sess_orphans.push_back({ol[4 * j], ol[4 * j + 1], ol[4 * j + 2], ol[4 * j + 3]});
     auto ct_of = [&](int64_t end) { return fw::cleanup_time(fw::jsub(end, 1), c.allowed_lateness); };
     std::vector<std::array<int64_t, 4>> keep;
     for (const auto& o : e->sess_orphans) if (ct_of(o[2]) > e->cur_wm) keep.push_back(o);
     e->sess_orphans.swap(keep);
-    // a restored timer that fired fetched its key's set (onEventTime -> getMergingWindowSet)
-    for (auto it = e->sess_rorphans.begin(); it != e->sess_rorphans.end();) {
-      const int64_t ct = ct_of((*it)[2]);
-      if (ct > e->cur_wm) { ++it; continue; }
-      int64_t ord = 0;
-      for (const auto& a : e->sess_adv) if (a.first >= ct) { ord = a.second; break; }
-      auto adj = e->sess_touch_adj.find((*it)[0]);
-      if (adj == e->sess_touch_adj.end() || std::make_pair(ord, ct) < adj->second) e->sess_touch_adj[(*it)[0]] = {ord, ct};
-      it = e->sess_rorphans.erase(it);
-    }
+    session_fire_rorphans(e);
+    // (intended ahead of the rejection: the drained entries are kept in sess_orphans, nothing is lost by a failing
+    // snapshot, and the log has room again)
+    // a dropped entry's timer is missing from the timers below until the watermark reaches it
+    if ((int64_t)lost > e->cur_wm)
+      return reject(e, FW_ERR_CAPACITY, "more purged sessions' cleanup timers pending than the orphan timer log holds (snapshots succeed again once the watermark passes the dropped ones)");
   }
   struct Pane { int64_t kid, key, start, end, sws, swc, put, cre, tre; bool trig; KgPane acc; int64_t lhead, llen; };
   std::vector<Pane> panes;
@@ -5928,6 +5983,7 @@ static int session_restore_kg_flink(fw_engine* e, int32_t kg, const fw_state_lay
         host_key_group(s, t[0]) != kg)
       return reject(e, FW_ERR_UNSUPPORTED, "timers differ from the ones the sessions imply");
     rorph.push_back({t[0], t[1], t[2]});
+    e->sess_rorph_ct = std::max(e->sess_rorph_ct, ct);
   }
   HIPCHK(e, hipSetDevice(e->dev));
   for (const auto& kv : mws) e->sess_mws_rank[kv.first] = (int64_t)e->sess_mws_rank.size();

@@ -776,13 +776,125 @@ __global__ __launch_bounds__(BLOCK) void k_sess_wm(Spec s, SessDev d, int64_t wm
   }
 }
 
-// the state entries k_sess_wm retired: namespace counts (and the shared-namespace log), a thread per entry
-__global__ __launch_bounds__(BLOCK) void k_sess_ns_retire(Spec s, SessDev d, int64_t touch_ord) {
+// the state entries k_sess_wm retired, a thread per entry: their namespace counts first, so that k_sess_log_roll
+// sees every namespace as this watermark leaves it.  (Sessions that began together mostly end together: logging each
+// removal as it is counted filled the log with entries of namespaces that ended at the same watermark.)  Also
+// zeroes the counts the next kernel and the next watermark start from
+__global__ __launch_bounds__(BLOCK) void k_sess_ns_retire(Spec s, SessDev d) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *d.nstmp_n = 0;
+    if (d.otmp_n) *d.otmp_n = 0;
+    *d.rlist_n2 = 0;
+  }
   const int64_t n = min((int64_t)*d.rlist_n, d.rlist_cap);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t x = d.rlist[i], kid = x / d.sw;
-    const int64_t key = kid_key(s, kid);
-    sess_ns_remove(d, record_key_group(s, long_hash_code(key)), key, x, touch_ord);
+    const int64_t x = d.rlist[i];
+    const int64_t key = kid_key(s, x / d.sw);
+    const uint64_t slot = sess_ns_slot(d, record_key_group(s, long_hash_code(key)), d.sws[x]);
+    atomicSub(&d.nscnt[slot], 1);
+    d.rslot[i] = (int64_t)slot;   // (k_sess_log_roll asks only this slot's count again)
+  }
+}
+
+// the checkpoint logs rolled over at a watermark into their spare buffers, which the host then makes the logs.
+// The last grid row, the namespace log: the entries whose hashed namespace still has live entries (an ended
+// instance is never asked for again), then the watermark's retired entries of such namespaces, removed at
+// touch_ord.  Row 0 of two, the orphan log: the entries whose cleanup time lies ahead of the watermark.  Any order:
+// snapshots order entries by their ordinals.  Nothing else appends to the logs meanwhile
+__global__ __launch_bounds__(BLOCK) void k_sess_log_roll(Spec s, SessDev d, int64_t wm, int64_t touch_ord) {
+  const bool ns = blockIdx.y + 1 == gridDim.y;   // (one row: the namespace log alone)
+  const int64_t* log = ns ? d.nslog : d.olog;
+  int64_t* tmp = ns ? d.nstmp : d.otmp;
+  unsigned long long* tn = ns ? d.nstmp_n : d.otmp_n;
+  const int64_t cap = ns ? d.nslog_cap : d.olog_cap;
+  const unsigned long long n0 = *(ns ? d.nslog_n : d.olog_n);
+  const int64_t n = (int64_t)min(n0, (unsigned long long)cap);   // (entries past the cap were dropped)
+  unsigned long long* gone = (unsigned long long*)&d.lmeta[ns ? LM_NSPRUNED : LM_OPRUNED];
+  if (blockIdx.x == 0 && threadIdx.x == 0 && n0 > (unsigned long long)n) atomicAdd(gone, n0 - (unsigned long long)n);
+  for (int64_t c0 = (int64_t)blockIdx.x * blockDim.x; c0 < n; c0 += (int64_t)gridDim.x * blockDim.x) {   // uniform per wave
+    const int64_t i = c0 + threadIdx.x;
+    int64_t v0 = 0, v1 = 0, v2 = 0, v3 = 0;
+    bool keep = false;
+    if (i < n) {
+      v0 = log[4 * i];
+      v1 = log[4 * i + 1];
+      v2 = log[4 * i + 2];
+      v3 = log[4 * i + 3];
+      keep = ns ? d.nscnt[sess_ns_slot(d, record_key_group(s, long_hash_code(v0)), v1)] > 0
+                : cleanup_time(jsub(v2, 1), d.late) > wm;
+    }
+    wave_count(gone, i < n && !keep);
+    const unsigned long long pos = wave_append(tn, keep);
+    if (keep && (int64_t)pos < cap) {
+      int64_t* l = tmp + 4 * pos;
+      l[0] = v0;
+      l[1] = v1;
+      l[2] = v2;
+      l[3] = v3;
+    } else if (keep) {   // (the namespace row only: this watermark's entries share the count) dropped, as sess_ns_log's
+      d.nsdrop[sess_ns_slot(d, record_key_group(s, long_hash_code(v0)), v1)] = 1;
+      d.lmeta[LM_NSDROP] = 1;
+    }
+  }
+  if (!ns) return;
+  // the retired entries still shared, appended with one addition to the log's count per workgroup: additions to one
+  // address are served one after the other, ~10 ns each on MI355X, and even a few entries in a hundred leave hardly
+  // a wave without one — a wave's (or, as the parent's k_sess_ns_retire, a thread's) addition each was ~100 us per
+  // 0.66 M entries.  So the workgroup counts its entries first, reserves their places, and walks them again
+  __shared__ unsigned int sh_n;   // the workgroup's entries to append; then the places handed out
+  __shared__ unsigned long long sh_base;
+  if (threadIdx.x == 0) sh_n = 0;
+  __syncthreads();
+  const int64_t nr = min((int64_t)*d.rlist_n, d.rlist_cap);
+  const int64_t gstride = (int64_t)gridDim.x * blockDim.x;
+  unsigned int mine = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nr; i += gstride) mine += d.nscnt[d.rslot[i]] > 0 ? 1u : 0u;
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&sh_n, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    sh_base = sh_n ? atomicAdd(d.nstmp_n, (unsigned long long)sh_n) : 0ull;
+    sh_n = 0;
+  }
+  __syncthreads();
+  const unsigned long long base = sh_base;
+  for (int64_t c0 = (int64_t)blockIdx.x * blockDim.x; c0 < nr; c0 += gstride) {   // uniform per wave
+    const int64_t i = c0 + threadIdx.x;
+    uint64_t slot = 0;
+    bool shared = false;
+    if (i < nr) {
+      slot = (uint64_t)d.rslot[i];
+      shared = d.nscnt[slot] > 0;   // (usually not: the namespace ended with this watermark)
+    }
+    const uint64_t mask = __ballot(shared);
+    if (mask == 0) continue;
+    const int leader = __ffsll((long long)mask) - 1;
+    unsigned int off = 0;
+    if ((int)(threadIdx.x & 63) == leader) off = atomicAdd(&sh_n, (unsigned int)__popcll(mask));
+    off = __shfl(off, leader);
+    if (!shared) continue;
+    const unsigned long long pos = base + off + (unsigned long long)__popcll(mask & lanemask_lt());
+    if ((int64_t)pos >= cap) {   // dropped, as sess_ns_log's
+      d.nsdrop[slot] = 1;
+      d.lmeta[LM_NSDROP] = 1;
+      continue;
+    }
+    const int64_t x = d.rlist[i];
+    int64_t* l = d.nstmp + 4 * pos;
+    l[0] = kid_key(s, x / d.sw);
+    l[1] = d.sws[x];
+    l[2] = d.swc[x];
+    l[3] = touch_ord;
+  }
+}
+
+// the namespaces a dropped log entry belonged to (SessDev::nsdrop): the ended ones forgotten, the live ones counted
+__global__ __launch_bounds__(BLOCK) void k_sess_ns_lost(SessDev d) {
+  const int64_t m = (int64_t)d.nsmask + 1;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+    if (!d.nsdrop[i]) continue;
+    if (d.nscnt[i] > 0) atomicAdd((unsigned long long*)&d.lmeta[LM_NSLIVE], 1ull);
+    else d.nsdrop[i] = 0;
   }
 }
 
@@ -873,15 +985,30 @@ int session_create(fw_engine* e) {
     while (m < 2 * (uint64_t)cells) m <<= 1;
     d.nsmask = m - 1;
     d.nscnt = e->alloc<int32_t>((size_t)m);
-    d.nslog_cap = std::max<int64_t>(1 << 16, 2 * e->cfg.max_batch);
+    // FW_SESS_LOG_CAP: both logs' capacity in entries, at least 64 (experiments and tests: a log filled by a few
+    // thousand records)
+    const char* lv = getenv("FW_SESS_LOG_CAP");
+    const int64_t lcap = lv ? std::max<int64_t>(64, atoll(lv)) : std::max<int64_t>(1 << 16, 2 * e->cfg.max_batch);
+    d.nslog_cap = lcap;
     d.nslog = e->alloc<int64_t>(4 * (size_t)d.nslog_cap);
     d.nslog_n = e->alloc<unsigned long long>(1);
-    d.olog_cap = std::max<int64_t>(1 << 16, 2 * e->cfg.max_batch);
+    d.olog_cap = lcap;
     d.olog = e->alloc<int64_t>(4 * (size_t)d.olog_cap);
     d.olog_n = e->alloc<unsigned long long>(1);
+    d.lmeta = e->alloc<long long>(LM_WORDS);
+    // the roll-overs' spare buffers: with the bookkeeping on, the orphan log's under PurgingTrigger with lateness only
+    const bool orph = e->cfg.trigger == FW_TRIGGER_PURGING_EVENT_TIME && e->cfg.allowed_lateness > 0;
+    d.otmp = d.ckpt && orph ? e->alloc<int64_t>(4 * (size_t)d.olog_cap) : nullptr;
+    d.otmp_n = d.ckpt && orph ? e->alloc<unsigned long long>(1) : nullptr;
+    d.nstmp = d.ckpt ? e->alloc<int64_t>(4 * (size_t)d.nslog_cap) : nullptr;
+    d.nstmp_n = d.ckpt ? e->alloc<unsigned long long>(1) : nullptr;
+    d.nsdrop = e->alloc<uint8_t>((size_t)m);
+    d.late = e->cfg.allowed_lateness;
     d.rlist_cap = (int64_t)cells;   // (a watermark retires at most every slot)
     d.rlist = e->alloc<int64_t>(cells);
+    d.rslot = d.ckpt ? e->alloc<int64_t>(cells) : nullptr;
     d.rlist_n = e->alloc<unsigned long long>(1);
+    d.rlist_n2 = e->alloc<unsigned long long>(1);
   }
   e->s.o.win_start = e->alloc<int64_t>((size_t)e->cfg.out_capacity);
   const size_t nb = (size_t)e->cfg.max_batch;
@@ -907,6 +1034,11 @@ int session_create(fw_engine* e) {
   HIPCHK(e, hipMemsetAsync(d.nslog_n, 0, 8, e->stream));
   HIPCHK(e, hipMemsetAsync(d.olog_n, 0, 8, e->stream));
   HIPCHK(e, hipMemsetAsync(d.rlist_n, 0, 8, e->stream));
+  HIPCHK(e, hipMemsetAsync(d.rlist_n2, 0, 8, e->stream));
+  HIPCHK(e, hipMemsetAsync(d.nsdrop, 0, (size_t)(d.nsmask + 1), e->stream));
+  const long long lmeta0[LM_WORDS] = {0, 0, INT64_MIN};   // LM_OLOST   // (no orphan entry dropped yet)
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpy(d.lmeta, lmeta0, sizeof lmeta0, hipMemcpyHostToDevice));
   return FW_OK;
 }
 
@@ -937,19 +1069,28 @@ int session_push(fw_engine* e, const BatchIn& b) {
 
 int session_watermark(fw_engine* e, int64_t wm) {
   if (wm > e->cur_wm) {
-    e->sess_adv.push_back({wm, e->ordinal});   // (checkpoints: when a restored orphan timer fired)
+    const bool orphans = e->sess.ckpt && e->cfg.trigger == FW_TRIGGER_PURGING_EVENT_TIME && e->cfg.allowed_lateness > 0;
+    const bool adv = orphans && !e->sess_rorphans.empty();
+    if (adv) e->sess_adv.push_back({wm, e->ordinal});   // (checkpoints: when a restored orphan timer fired)
     e->phase_begin(FW_PHASE_FIRE);
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((e->s.stride + BLOCK - 1) / BLOCK, e->grid));
     if (e->sess.nw == 1) hipLaunchKernelGGL(k_sess_wm<1>, dim3(blocks), dim3(BLOCK), 0, e->stream, e->s, e->sess, wm, e->ordinal);
     else if (e->sess.nw == 2) hipLaunchKernelGGL(k_sess_wm<2>, dim3(blocks), dim3(BLOCK), 0, e->stream, e->s, e->sess, wm, e->ordinal);
     else hipLaunchKernelGGL(k_sess_wm<4>, dim3(blocks), dim3(BLOCK), 0, e->stream, e->s, e->sess, wm, e->ordinal);
     if (e->sess.ckpt) {
-      hipLaunchKernelGGL(k_sess_ns_retire, dim3(e->grid), dim3(BLOCK), 0, e->stream, e->s, e->sess, e->ordinal);
-      HIPCHK(e, hipMemsetAsync(e->sess.rlist_n, 0, 8, e->stream));
+      SessDev& d = e->sess;
+      const int rows = orphans ? 2 : 1;   // (the orphan log is written under PurgingTrigger with lateness only)
+      hipLaunchKernelGGL(k_sess_ns_retire, dim3(e->grid), dim3(BLOCK), 0, e->stream, e->s, d);
+      hipLaunchKernelGGL(k_sess_log_roll, dim3(e->grid, rows), dim3(BLOCK), 0, e->stream, e->s, d, wm, e->ordinal);
+      std::swap(d.nslog, d.nstmp);   // the spare buffers are the logs from here on
+      std::swap(d.nslog_n, d.nstmp_n);
+      if (orphans) { std::swap(d.olog, d.otmp); std::swap(d.olog_n, d.otmp_n); }
+      std::swap(d.rlist_n, d.rlist_n2);
     }
     e->phase_end(e->s.stride);
     session_pool_recycle(e);   // the entries of the windows purged
     e->cur_wm = wm;
+    if (adv && wm >= e->sess_rorph_ct) session_fire_rorphans(e);   // the last restored timer fired: sess_adv ends
     hipLaunchKernelGGL(k_mark_only, dim3(1), dim3(1), 0, e->stream, e->s, wm);
     e->hmarks.push_back({wm, e->dev_marks++, true});
     e->out_dirty = false;
@@ -961,5 +1102,46 @@ int session_watermark(fw_engine* e, int64_t wm) {
     e->hmarks.push_back({wm, e->dev_marks - 1, false});
   }
   HIPCHK(e, hipGetLastError());
+  return FW_OK;
+}
+
+// whether a namespace still live lacks a log entry that found the log full: snapshots fail until it has ended
+int session_ns_lost(fw_engine* e, bool* lossy) {
+  const SessDev& d = e->sess;
+  *lossy = false;
+  long long meta[LM_WORDS];
+  HIPCHK(e, hipMemcpy(meta, d.lmeta, sizeof meta, hipMemcpyDeviceToHost));
+  if (!meta[LM_NSDROP]) return FW_OK;
+  HIPCHK(e, hipMemsetAsync(d.lmeta + LM_NSLIVE, 0, 8, e->stream));
+  hipLaunchKernelGGL(k_sess_ns_lost, dim3(e->grid), dim3(BLOCK), 0, e->stream, d);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpy(meta, d.lmeta, sizeof meta, hipMemcpyDeviceToHost));
+  if (meta[LM_NSLIVE] > 0) *lossy = true;
+  else HIPCHK(e, hipMemset(d.lmeta + LM_NSDROP, 0, 8));   // every such namespace has ended
+  return FW_OK;
+}
+
+int fw_debug_session_logs(fw_engine* e, int64_t* out8) {
+  if (!e || !out8) return FW_ERR_INVALID_ARG;
+  if (!e->session) return FW_ERR_UNSUPPORTED;
+  const SessDev& d = e->sess;
+  HIPCHK(e, hipSetDevice(e->dev));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  bool ns_lossy = false;
+  if (int rc = session_ns_lost(e, &ns_lossy)) return rc;
+  unsigned long long no = 0, nl = 0;
+  long long meta[LM_WORDS];
+  HIPCHK(e, hipMemcpy(&no, d.olog_n, 8, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(&nl, d.nslog_n, 8, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(meta, d.lmeta, sizeof meta, hipMemcpyDeviceToHost));
+  out8[0] = d.olog_cap;
+  out8[1] = d.nslog_cap;
+  out8[2] = std::min<int64_t>((int64_t)no, d.olog_cap);
+  out8[3] = std::min<int64_t>((int64_t)nl, d.nslog_cap);
+  out8[4] = (int64_t)meta[LM_OPRUNED] + e->sess_olog_drained + (int64_t)no;   // appended, the dropped ones included
+  out8[5] = (int64_t)meta[LM_NSPRUNED] + (int64_t)nl;
+  out8[6] = (int64_t)e->sess_adv.size();
+  out8[7] = (ns_lossy || (int64_t)meta[LM_OLOST] > e->cur_wm) ? 1 : 0;
   return FW_OK;
 }

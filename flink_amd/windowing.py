@@ -537,6 +537,16 @@ class WindowEngine:
         self._check(self._fn("get_stats")(self.h, ctypes.byref(st)))
         return {k: getattr(st, k) for k, _ in _abi.FwStats._fields_}
 
+    def session_logs(self):
+        """fw_debug_session_logs: the session checkpoints' device logs (orphan = purged sessions' cleanup timers,
+        namespace = removals from shared "window-contents" namespaces): capacities, entries held, entries ever
+        appended, the host's advance list, and whether snapshots currently fail because a log dropped an entry."""
+        out = np.zeros(8, np.int64)
+        self._check(self._fn("debug_session_logs")(self.h, ctypes.c_void_p(out.ctypes.data)))
+        names = ("orphan_cap", "namespace_cap", "orphan_entries", "namespace_entries", "orphan_appended",
+                 "namespace_appended", "advances", "lossy")
+        return dict(zip(names, (int(v) for v in out)))
+
     def close(self):
         if self.h:
             self._fn("destroy")(self.h)

@@ -412,6 +412,14 @@ int         fw_stream_wait_input(fw_engine* e, void* stream, int32_t back);
 
 /* diagnostics: raw device counters (8 x int64) */
 int         fw_debug_counters(fw_engine* e, int64_t* out8);
+/* diagnostics: the session checkpoints' two device logs (purged sessions' cleanup timers; entries removed from a
+ * shared "window-contents" namespace).  out8: the orphan log's capacity [0] and the namespace log's [1] in entries
+ * (FW_SESS_LOG_CAP in the environment at creation overrides both), the entries each holds now [2] [3], the entries
+ * ever appended to each, pruned and dropped ones included [4] [5], the length of the host's watermark-advance
+ * list [6], and whether a log has dropped an entry a snapshot still needs [7]: while it has, snapshots in the
+ * reference layout fail with FW_ERR_CAPACITY.  Synchronises.  Session windows only.  Not strictly read-only: to
+ * answer [7] it makes the scan a snapshot makes, which forgets the dropped entries of namespaces that have ended. */
+int         fw_debug_session_logs(fw_engine* e, int64_t* out8);
 /* diagnostics: per-workgroup phase timestamps of the partitioned ingest (engine created with
  * FW_DEBUG_AGG & 16 in the environment); n int64 values, 100 MHz realtime clock */
 int         fw_debug_stamps(fw_engine* e, int64_t* out, int64_t n);

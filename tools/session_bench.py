@@ -5,7 +5,9 @@ of fw_session.hip's per-key walk.
 
 Workload (env overrides): SB_KEYS keys (default 65536), SB_RATE events per event-time second (default 2^22, so
 ~64 events per key per second, ~16 ms apart), SB_GAP session gap in ms (default 10: mostly 1-3 record sessions
-that fire as the watermark passes), SB_BATCH events per push (default 2^20), SB_ZIPF (unset: uniform keys).
+that fire as the watermark passes), SB_BATCH events per push (default 2^20), SB_ZIPF (unset: uniform keys),
+SB_PURGING=1 (PurgingTrigger) and SB_LATENESS allowed lateness in ms (default 0): together the configuration whose
+purged sessions' cleanup timers are logged for checkpoints.
 Check: after the final MAX watermark the wrapping sum of the fired sums equals that of the values pushed.
 """
 import json
@@ -17,7 +19,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flink_amd.synth import stream  # noqa: E402
-from flink_amd.windowing import EventTimeSessionWindows, ReduceFunction, WindowEngine, make_config  # noqa: E402
+from flink_amd.windowing import (EventTimeSessionWindows, EventTimeTrigger, PurgingTrigger, ReduceFunction,  # noqa: E402
+                                 WindowEngine, make_config)
 
 LONG_MAX = (1 << 63) - 1
 T0 = 1_700_000_000_000
@@ -31,8 +34,11 @@ def main():
     zipf = float(os.environ["SB_ZIPF"]) if os.environ.get("SB_ZIPF") else None
     steps, warmup = int(os.environ.get("SB_STEPS", 16)), int(os.environ.get("SB_WARMUP", 4))
     slots = int(os.environ.get("SB_SLOTS", 32))
+    purging = os.environ.get("SB_PURGING", "0") == "1"
+    lateness = int(os.environ.get("SB_LATENESS", 0))
+    trig = PurgingTrigger.of(EventTimeTrigger.create()) if purging else EventTimeTrigger.create()
     dev = "cuda"
-    cfg = make_config(EventTimeSessionWindows.withGap(gap), ReduceFunction(("sum",), "i64", True),
+    cfg = make_config(EventTimeSessionWindows.withGap(gap), ReduceFunction(("sum",), "i64", True), trig, lateness,
                       max_parallelism=128, key_capacity=keys, max_batch=batch, max_open_slices=slots,
                       out_capacity=batch * (steps + warmup + 2))
     eng = WindowEngine(cfg)
@@ -67,7 +73,7 @@ def main():
     line = {"metric": "events/s keyed event-time session windows (sum, f1 = first arrival)",
             "value": steps * batch / dt, "unit": "events/s", "ms_per_step": dt * 1e3 / steps, "steps": steps,
             "config": {"keys": keys, "rate_per_s": rate, "gap_ms": gap, "batch": batch, "zipf": zipf,
-                       "slots_per_key": slots},
+                       "slots_per_key": slots, "purging": purging, "lateness_ms": lateness},
             "sessions_fired": int(st["panes_fired"]), "check": "ok" if fired == pushed else "MISMATCH",
             "data": "synthetic (splitmix64 counter stream), resident in HBM"}
     print(json.dumps(line), flush=True)
