@@ -8,7 +8,9 @@
 //     into a fresh oracle, snapshotted again: identical bytes), and the wire-format decoder (whole and cut
 //     streams, a corrupt tag);
 //   - flink_kg_format.h, the engine's host-side checkpoint codec: big-endian writer / reader round trips,
-//     reads past the end (ok = false), HashMap iteration order over random tables.
+//     reads past the end (ok = false), HashMap iteration order over random tables; its section layer: timer
+//     sections and "window-contents" tables (reducing and list state) written, read and written back, every
+//     strict prefix of a section in a buffer of exactly its size, corrupt counts and key fields, the copy-out.
 // Any sanitizer report aborts with a non-zero status; the test asserts status 0.
 #include <cinttypes>
 #include <cstdio>
@@ -191,8 +193,174 @@ static void kg_codec() {
   }
 }
 
+// a section cut to `len` bytes in a buffer of exactly that size, so that any read past it is an ASan report
+static std::vector<uint8_t> cut(const std::vector<uint8_t>& b, size_t len) {
+  return std::vector<uint8_t>(b.begin(), b.begin() + (ptrdiff_t)len);
+}
+
+// timer sections: set order, write / read round trips, cut and padded sections, the two corrupt counts
+static void kg_timer_sections() {
+  using fwkg::Timer;
+  using fwkg::TimersFail;
+  for (size_t n : {(size_t)0, (size_t)1, (size_t)2, (size_t)12, (size_t)13, (size_t)14, (size_t)30, (size_t)100}) {
+    for (uint64_t round = 0; round < 4; ++round) {
+      std::vector<Timer> t(n);
+      for (size_t i = 0; i < n; ++i) {
+        const int64_t start = (int64_t)(splitmix(round * 131 + i) % 50) * 1000 - 7000;
+        t[i] = {(int64_t)i * 1000003 - 4000, start, start + 1000, start + 999 + (int64_t)(i % 2) * 250};   // (keys ascend)
+      }
+      // half of them restored, in reverse order: they lead their buckets in rank order
+      std::map<Timer, int64_t> rank;
+      if (round & 1) for (size_t i = 0; i < n; i += 2) rank[t[i]] = (int64_t)(n - i);
+      const std::vector<Timer> ordered =
+          fwkg::timers_in_set_order(n, [&](size_t i) { return t[i]; }, rank, [](size_t a, size_t b) { return a < b; });
+      CHECK(ordered.size() == n);
+      std::vector<Timer> a = t, b = ordered;
+      std::sort(a.begin(), a.end());
+      std::sort(b.begin(), b.end());
+      CHECK(a == b);
+      const uint32_t mask = fwkg::capacity_for(n) - 1;
+      CHECK(n <= 12 ? mask == 15 : mask >= 31);   // more than 12 entries: the table doubled
+      for (size_t i = 1; i < n; ++i) {
+        const Timer &x = ordered[i - 1], &y = ordered[i];
+        const uint32_t bx = (uint32_t)fwkg::spread(fwkg::timer_hash(x.ts, x.key, x.start, x.end)) & mask;
+        const uint32_t by = (uint32_t)fwkg::spread(fwkg::timer_hash(y.ts, y.key, y.start, y.end)) & mask;
+        CHECK(bx <= by);
+        if (bx != by) continue;
+        const bool rx = rank.count(x) != 0, ry = rank.count(y) != 0;
+        CHECK(rx || !ry);                             // restored ones first
+        if (rx && ry) CHECK(rank[x] < rank[y]);       // in blob order
+        if (!rx && !ry) CHECK(x.key < y.key);         // then the caller's order (keys ascend with the index)
+      }
+      fwkg::BeOut o;
+      fwkg::write_timers(o, ordered);
+      CHECK(o.b.size() == 8 + 32 * n);
+      std::vector<Timer> back;
+      CHECK(fwkg::read_timers(o.b.data(), (int64_t)o.b.size(), back) == TimersFail::none);
+      CHECK(back == ordered);
+      for (size_t len = 0; len < o.b.size(); ++len) {
+        const std::vector<uint8_t> c = cut(o.b, len);
+        CHECK(fwkg::read_timers(c.data(), (int64_t)len, back) == TimersFail::truncated_or_trailing);
+        CHECK(back.size() <= n);
+      }
+      std::vector<uint8_t> more = o.b;
+      more.push_back(0);
+      CHECK(fwkg::read_timers(more.data(), (int64_t)more.size(), back) == TimersFail::truncated_or_trailing);
+      std::vector<uint8_t> neg = o.b;
+      neg[0] = 0x80;
+      CHECK(fwkg::read_timers(neg.data(), (int64_t)neg.size(), back) == TimersFail::negative_count);
+      std::vector<uint8_t> proc = o.b;
+      proc.back() = 1;
+      CHECK(fwkg::read_timers(proc.data(), (int64_t)proc.size(), back) == TimersFail::processing_timers);
+    }
+  }
+}
+
+// "window-contents" tables: what a table's reader yields, written back in that (insertion) order, is the table
+struct WcModel {
+  struct Ent { int64_t start, end; fwkg::WcEntry e; };
+  std::vector<Ent> ents;
+};
+static fwkg::WcFail wc_read(const std::vector<uint8_t>& b, const fwkg::WcLayout& L, WcModel& m) {
+  m.ents.clear();
+  fwkg::BeIn in(b.data(), (int64_t)b.size());
+  const fwkg::WcFail f = fwkg::read_window_contents(
+      in, L, [](int64_t, int64_t) { return true; },
+      [&](int64_t s, int64_t e, fwkg::WcEntry& ent) { m.ents.push_back({s, e, ent}); return true; });
+  return f == fwkg::WcFail::none && !in.done() ? fwkg::WcFail::truncated : f;
+}
+static std::vector<uint8_t> wc_write(const WcModel& m, const fwkg::WcLayout& L) {
+  std::vector<fwkg::WcNamespace> ns =
+      fwkg::group_namespaces(m.ents.size(), [&](size_t i) { return std::make_pair(m.ents[i].start, m.ents[i].end); });
+  std::vector<size_t> first(ns.size());
+  for (size_t w = 0; w < ns.size(); ++w) first[w] = ns[w].entries[0];
+  fwkg::BeOut o;
+  fwkg::write_window_contents(
+      o, L, ns, [&](size_t a, size_t b) { return first[a] < first[b]; }, [&](size_t i) { return m.ents[i].e.key; },
+      [](size_t a, size_t b) { return a < b; },
+      [&](size_t i, fwkg::WcEntry& ent) { ent.word = m.ents[i].e.word; ent.el = m.ents[i].e.el; });
+  return o.b;
+}
+static void kg_window_contents() {
+  const int32_t reduce_fields[4] = {FW_SF_KEY, FW_SF_F1, FW_SF_SUM, FW_SF_MAX};
+  const int32_t list_fields[3] = {FW_SF_KEY, FW_SF_VALUE, FW_SF_F1};
+  const fwkg::WcLayout layouts[2] = {{reduce_fields, 4, false}, {list_fields, 3, true}};
+  for (const fwkg::WcLayout& L : layouts) {
+    for (uint64_t round = 0; round < 6; ++round) {
+      // several namespaces sharing keys, entries in a scrambled insertion order
+      WcModel m;
+      const int n_ns = (int)(round % 4), n_keys = 1 + (int)(splitmix(round) % 20);
+      for (int k = 0; k < n_keys; ++k)
+        for (int w = 0; w < n_ns; ++w) {
+          if (splitmix(round * 7 + (uint64_t)(k * 5 + w)) % 3 == 0) continue;
+          WcModel::Ent x;
+          x.start = (int64_t)w * 1000 - 1000;
+          x.end = x.start + 1000;
+          x.e.key = (int64_t)(splitmix((uint64_t)k + 99) >> (k % 2 ? 33 : 1)) - (k % 3 ? 0 : INT64_MAX / 2);
+          if (L.list) {
+            const int nel = 1 + (int)(splitmix((uint64_t)(k + w)) % 4);
+            for (int q = 0; q < nel; ++q) x.e.el.push_back({(int64_t)splitmix(round + (uint64_t)q), (int64_t)(k * 10 + q)});
+          } else {
+            for (int f = 0; f < L.n_fields; ++f)
+              x.e.word.push_back(L.field[f] == FW_SF_KEY ? x.e.key : (int64_t)splitmix(round * 13 + (uint64_t)(k * 4 + f)));
+          }
+          m.ents.insert(m.ents.begin() + (ptrdiff_t)(splitmix(round + m.ents.size()) % (m.ents.size() + 1)), x);
+        }
+      const std::vector<uint8_t> b = wc_write(m, L);
+      WcModel back;
+      CHECK(wc_read(b, L, back) == fwkg::WcFail::none);
+      CHECK(back.ents.size() == m.ents.size());
+      size_t found = 0;
+      for (const auto& x : back.ents)
+        for (const auto& y : m.ents)
+          if (x.start == y.start && x.end == y.end && x.e.key == y.e.key) { CHECK(x.e.word == y.e.word && x.e.el == y.e.el); ++found; }
+      CHECK(found == m.ents.size());
+      CHECK(wc_write(back, L) == b);   // restored in blob order, the table is written back unchanged
+      for (size_t len = 0; len < b.size(); ++len) CHECK(wc_read(cut(b, len), L, back) == fwkg::WcFail::truncated);
+    }
+  }
+  // hand-built corrupt tables: one namespace [0, 1000), one entry of key 7
+  auto table = [&](bool list, int32_t n_ns, int32_t n_ent, int32_t n_el, int64_t key_field) {
+    fwkg::BeOut o;
+    o.i32(n_ns); o.i64(0); o.i64(1000); o.i32(n_ent); o.i64(7);
+    if (list) { o.i32(n_el); for (int q = 0; q < n_el; ++q) { o.i64(key_field); o.i64(40 + q); o.i64(50 + q); } }
+    else { o.i64(key_field); o.i64(1); o.i64(2); o.i64(3); }
+    return o.b;
+  };
+  WcModel back;
+  CHECK(wc_read(table(false, 1, 1, 0, 7), layouts[0], back) == fwkg::WcFail::none && back.ents.size() == 1);
+  CHECK(wc_read(table(false, 1, 1, 0, 8), layouts[0], back) == fwkg::WcFail::entry_key_differs);
+  CHECK(wc_read(table(false, -1, 1, 0, 7), layouts[0], back) == fwkg::WcFail::negative_count);
+  CHECK(wc_read(table(false, 1, -5, 0, 7), layouts[0], back) == fwkg::WcFail::negative_count);
+  CHECK(wc_read(table(true, 1, 1, 2, 7), layouts[1], back) == fwkg::WcFail::none && back.ents.size() == 1 &&
+        back.ents[0].e.el.size() == 2 && back.ents[0].e.el[1][0] == 41 && back.ents[0].e.el[1][1] == 51);
+  CHECK(wc_read(table(true, 1, 1, 2, 8), layouts[1], back) == fwkg::WcFail::element_key_differs);
+  CHECK(wc_read(table(true, 1, 1, 0, 7), layouts[1], back) == fwkg::WcFail::empty_list);
+  CHECK(wc_read(table(true, 1, 1, -1, 7), layouts[1], back) == fwkg::WcFail::negative_list_size);
+  // a callback that stops the read; the copy-out's size query, short buffers and an empty state section
+  {
+    const std::vector<uint8_t> b = table(false, 1, 1, 0, 7);
+    fwkg::BeIn in(b.data(), (int64_t)b.size());
+    CHECK(fwkg::read_window_contents(in, layouts[0], [](int64_t, int64_t) { return false; },
+                                     [](int64_t, int64_t, fwkg::WcEntry&) { return true; }) == fwkg::WcFail::stopped);
+    fwkg::BeOut st, tm, none;
+    st.i64(1); st.u8(2);
+    fwkg::write_timers(tm, {});
+    int64_t ls = -1, lt = -1;
+    CHECK(fwkg::copy_sections(st, tm, nullptr, 0, &ls, nullptr, 0, &lt) && ls == 9 && lt == 8);
+    std::vector<uint8_t> bs(9), bt(8);
+    CHECK(!fwkg::copy_sections(st, tm, bs.data(), 8, &ls, bt.data(), 8, &lt) && ls == 9);
+    CHECK(!fwkg::copy_sections(st, tm, bs.data(), 9, &ls, bt.data(), 7, &lt));
+    CHECK(!fwkg::copy_sections(st, tm, bs.data(), 9, &ls, nullptr, 0, &lt));
+    CHECK(fwkg::copy_sections(st, tm, bs.data(), 9, &ls, bt.data(), 8, &lt) && bs == st.b && bt == tm.b);
+    CHECK(fwkg::copy_sections(none, tm, bs.data(), 0, &ls, bt.data(), 8, &lt) && ls == 0);
+  }
+}
+
 int main() {
   kg_codec();
+  kg_timer_sections();
+  kg_window_contents();
   decode_streams();
   // the window shapes
   struct Case { int assigner; int64_t size, slide, lateness; int trigger, agg, flags, vt, first; };

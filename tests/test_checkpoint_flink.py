@@ -398,6 +398,80 @@ def test_restore_rejections():
     e.close()
 
 
+def _prefix_lengths(n):
+    """Every strict prefix length >= 1 of an n-byte section; past 512 of them, the first and the last 256."""
+    lens = list(range(1, n))
+    return lens if len(lens) <= 512 else lens[:256] + lens[-256:]
+
+
+def _truncation_inputs():
+    """(name, config, layout, restore watermark, every key group's sections) for the smallest tumbling-reduce, list
+    and session checkpoints the suite builds, each written by the engine itself."""
+    from flink_amd.windowing import WindowEngine
+    import test_session_checkpoint as ts_
+    sc = SCEN["tumbling_lateness_i64"]
+    e = WindowEngine(_cfg(sc))
+    _drive(e, sc, 0, sc["cut"])
+    snaps = _snapshot_all(e, sc)
+    e.close()
+    yield "tumbling_lateness_i64", _cfg(sc), sc["layout"], _restore_wm(sc), snaps
+    list_cfg, *_, list_wm = _list_setup("i64", 0, 1)
+    yield "list", list_cfg, ("key", "f1", "value"), list_wm, _list_run(WindowEngine, "i64", 0, 1)
+    case = ts_.CASES[2]   # (two aggregates, no lateness: the shortest entries and one timer per session)
+    keys, ts, _, _ = ts_._stream(case[0])
+    wm2 = int(ts[:int(len(keys) * 2 / 3)].max()) - 100   # (_run's second snapshot)
+    yield "session", ts_._config(*case), ts_._layout(case[1]), wm2, ts_._run(WindowEngine, case)[0][-1]
+
+
+@pytest.mark.gpu
+def test_truncated_sections_rejected():
+    """A restore of a state or timer section cut short — every strict prefix (of a long section: the first and the
+    last 256), the other section intact — is rejected with FW_ERR_INVALID_ARG by the host's parsing, for a tumbling
+    reduce, a list and a session checkpoint; the engine stays usable: it then restores the intact sections of every
+    key group and writes them back unchanged.
+    One prefix length differs by design of the session layout's reader: a section cut inside the 2-byte id of its
+    second table ("merging-window-set") reads that id as 0 and is refused as keyed state it does not know
+    (FW_ERR_UNSUPPORTED) — as before the section codec moved into flink_kg_format.h."""
+    from flink_amd import _abi
+    from flink_amd.windowing import WindowEngine
+    tried = 0
+    for name, cfg, layout, wm, snaps in _truncation_inputs():
+        kg = max(snaps, key=lambda k: len(snaps[k][0]))
+        st, tm = snaps[kg]
+        assert len(st) > 11 and len(tm) > 8, name
+        e = WindowEngine(cfg)
+        for part, section in (("state", st), ("timers", tm)):
+            for n in _prefix_lengths(len(section)):
+                with pytest.raises(_abi.FwError) as ei:
+                    if part == "state":
+                        e.restore_kg_flink(kg, layout, section[:n], tm, wm)
+                    else:
+                        e.restore_kg_flink(kg, layout, st, section[:n], wm)
+                want = _abi.FW_ERR_INVALID_ARG
+                if name == "session" and part == "state" and n == _second_table_at(section) + 1:
+                    want = _abi.FW_ERR_UNSUPPORTED
+                assert ei.value.code == want, (name, part, n, len(section), ei.value.code, str(ei.value))
+                tried += 1
+        for k, (s, t) in snaps.items():
+            e.restore_kg_flink(k, layout, s, t, wm)
+        back = {k: e.snapshot_kg_flink(k, layout) for k in snaps}
+        e.close()
+        assert _diff(back, snaps) is None, (name, _diff(back, snaps))
+    assert tried > 1000
+
+
+def _second_table_at(st):
+    """Offset of the second state table's id in a session key group's state section (present window-contents table
+    of ("key", "f1", two aggregates) entries first)."""
+    assert struct.unpack(">hb", st[4:7]) == (0, 1)
+    (nns,), pos = struct.unpack(">i", st[7:11]), 11
+    for _ in range(nns):
+        (ne,) = struct.unpack(">i", st[pos + 16:pos + 20])
+        pos += 20 + ne * 8 * 5
+    assert struct.unpack(">h", st[pos:pos + 2]) == (1,)
+    return pos
+
+
 def _purging_lateness_run(factory_g, mode, restore_at, sliding=False):
     """PurgingTrigger + allowed lateness 400 (tumbling 1 s): a window's fire purges its state but each key keeps its
     cleanup timer until maxTimestamp + 400 (WindowOperator.java:365-371 clears the contents only; the timer is
@@ -678,20 +752,26 @@ def test_fold_checkpoint(mode, kind, initial, vt, assigner):
                                               for x, y in zip(rg, ro)), w
 
 
-def _list_run(factory, vt, lateness, mode, restore=None, layout=("key", "f1", "value"), restore_wm=None, pre=None,
-              sliding=False, slide=1000):
-    """List state (WindowedStream.apply: HeapListState "window-contents" of the input tuples), tumbling 1 s windows
-    or (sliding) 3 s windows every 1 s: drive 2/3 of a Zipf stream, snapshot every key group in the reference
-    layout; or restore such sections at their watermark and drive the rest to a final MAX_WATERMARK."""
+def _list_setup(vt, lateness, mode, sliding=False, slide=1000):
+    """_list_run's config, stream, checkpoint position and checkpoint watermark."""
     from flink_amd.windowing import ListStateDescriptor, SlidingEventTimeWindows, TumblingEventTimeWindows, make_config
-    from harness import drive, gen_stream
+    from harness import gen_stream
     keys, ts, vals = gen_stream(24_000, 1200, rate=1 << 13, zipf=1.1, ooo=300, value_type=vt)
     f1 = np.arange(len(keys), dtype=np.int64) * 7 + 3
     asg = SlidingEventTimeWindows.of(3000, slide) if sliding else TumblingEventTimeWindows.of(1000)
     cfg = make_config(asg, ListStateDescriptor(vt), None, lateness, max_parallelism=128,
                       key_capacity=1 << 12, max_batch=1 << 12, out_capacity=1 << 20, ingest_mode=mode)
     n = len(keys) * 2 // 3
-    wm = int(ts[:n].max()) - 100
+    return cfg, keys, ts, vals, f1, n, int(ts[:n].max()) - 100
+
+
+def _list_run(factory, vt, lateness, mode, restore=None, layout=("key", "f1", "value"), restore_wm=None, pre=None,
+              sliding=False, slide=1000):
+    """List state (WindowedStream.apply: HeapListState "window-contents" of the input tuples), tumbling 1 s windows
+    or (sliding) 3 s windows every 1 s: drive 2/3 of a Zipf stream, snapshot every key group in the reference
+    layout; or restore such sections at their watermark and drive the rest to a final MAX_WATERMARK."""
+    from harness import drive
+    cfg, keys, ts, vals, f1, n, wm = _list_setup(vt, lateness, mode, sliding, slide)
     e = factory(cfg)
     if restore is None:
         drive(e, keys[:n], ts[:n], vals[:n], 2048, 100, None, f1=f1[:n])
